@@ -218,6 +218,34 @@ def _emit_final():
     print(_FINAL[-1], flush=True)
 
 
+DUMP_LIMIT = 64 << 20     # bytes of --dump-outputs in all
+
+
+def _records(recs, seeds=None):
+    """pose records as the caller of the ICP path receives them (capi Result dicts) -> one array per field"""
+    out = {k: np.stack([np.asarray(r[k], dtype=np.float64) for r in recs]) for k in ("T", "T_raw", "norm", "rmse")}
+    out.update({k: np.array([r[k] for r in recs], dtype=np.float64) for k in ("inliers", "status", "iterations", "n_src", "n_tgt")})
+    if seeds is not None:
+        out["seed"] = np.array(seeds, dtype=np.float64)
+    return out
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array, float32 where the path returns float32, float64 otherwise.  Past DUMP_LIMIT
+    bytes in all, an array keeps a fixed, seeded sample of its rows (the same rows for the same shapes), listed in <name>_rows.npy."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32 if np.asarray(v).dtype == np.float32 else np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    for k, a in arrays.items():
+        if total > DUMP_LIMIT and a.ndim >= 1 and a.shape[0] > 1:
+            # a third of the budget for the data: the row indices (8 B each) of 4-byte rows take twice as much again
+            keep = max(1, int(a.shape[0] * (DUMP_LIMIT // 3) / total))
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))
+            np.save(os.path.join(path, f"{k}_rows.npy"), rows.astype(np.float64))
+            a = a[rows]
+        np.save(os.path.join(path, f"{k}.npy"), a)
+
+
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -253,6 +281,9 @@ def parse_args():
     ap.add_argument("--one-device", action="store_true")
     ap.add_argument("--force-collective", action="store_true", help="developer knob: run the RCCL exchanges even with one rank")
     ap.add_argument("--no-pipeline", action="store_true", help="one handle, every alignment fetched before the next is queued")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="rank 0 writes what the timed path returned in its LAST timed step as DIR/<name>.npy (float32/float64, "
+                         "at most 64 MB in all); same arguments, same inputs: two builds can be compared output for output")
     ap.add_argument("--dump-table", default="", help="rank 0 writes the LAST step's gathered pose table (pair order) with every record's seed "
                     "to this JSON file (tests: BASELINE config 4's shape, --gpus 8 --pairs 64 --pairs-per-step 64 --in-flight 1 --pool 64)")
     ap.add_argument("--in-flight", type=int, default=8, help="alignments in flight (handles taking turns, one HIP stream each; the runtime has "
@@ -721,9 +752,10 @@ def h2d_rate(torch, dist, world, pool, dev, reps=24):
     return reps * pool.depth.numel() * 2 / (time.perf_counter() - t0) / 1e9
 
 
-def timed_stream(torch, dist, world, streamer, steps, warmup, aligns_per_step, comm=None, P=1):
+def timed_stream(torch, dist, world, streamer, steps, warmup, aligns_per_step, comm=None, P=1, last=None):
     """W untimed steps, then EXACTLY K steps between barrier + synchronize; the pose records of every step are
-    gathered over RCCL (pipelined by one step, last table collected before the clock stops)."""
+    gathered over RCCL (pipelined by one step, last table collected before the clock stops).  `last`, a list: receives
+    this rank's records of the last timed step (their seeds in `.seeds`)."""
     def fence():
         torch.cuda.synchronize()
         if world > 1:
@@ -738,10 +770,10 @@ def timed_stream(torch, dist, world, streamer, steps, warmup, aligns_per_step, c
     class _Sink(list):
         pass
 
-    def one_step():
+    def one_step(keep=False):
         nonlocal pending, table, step_seeds
         sink = None
-        if comm is not None:
+        if comm is not None or keep:
             sink = _Sink(); sink.seeds = []
         res = streamer.run(aligns_per_step, sink)
         if sink is not None:
@@ -752,6 +784,8 @@ def timed_stream(torch, dist, world, streamer, steps, warmup, aligns_per_step, c
                 table = comm.gather_collect(aligns_per_step * P); pending -= 1
             comm.gather_submit(sink); pending += 1
             tg[0] += time.perf_counter() - t0; tg[1] += 1
+        if keep:
+            last[:] = [sink]
         return res
 
     def drain():
@@ -769,8 +803,8 @@ def timed_stream(torch, dist, world, streamer, steps, warmup, aligns_per_step, c
     streamer.t_enqueue = streamer.t_fetch = 0.0; streamer.n_enqueued = 0
     tg[0], tg[1] = 0.0, 0
     t0 = time.perf_counter()
-    for _ in range(steps):
-        res = one_step()
+    for i in range(steps):
+        res = one_step(last is not None and i == steps - 1)
     drain()                 # the last step's pose table is on every rank before the clock stops
     fence()
     el = time.perf_counter() - t0
@@ -811,6 +845,13 @@ def seg_mode(args, torch, dist, capi, synth, world, rank, local_rank, dev):
         out_planes = h.segment_planes_device(ptrs, sp, d_lab.data_ptr(), stream)
     fence()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        fl = [(f, pl) for f, fp in enumerate(out_planes) for pl in fp]
+        dump_outputs(args.dump_outputs, {"plane_frame": np.array([f for f, _ in fl], dtype=np.float64).reshape(-1),
+                                         "plane_coeff": np.array([pl["coeff"] for _, pl in fl], dtype=np.float32).reshape(-1, 4),
+                                         "plane_count": np.array([pl["count"] for _, pl in fl], dtype=np.float64).reshape(-1),
+                                         "plane_centroid": np.array([pl["centroid"] for _, pl in fl], dtype=np.float32).reshape(-1, 3),
+                                         "labels": d_lab.cpu().numpy()})
     if world > 1:
         tmax = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -879,6 +920,9 @@ def voxel_mode(args, torch, dist, capi, synth, world, rank, local_rank, dev):
         m = h.voxel_grid_device(d.data_ptr(), n, out_d.data_ptr(), 0.03, stream)
     fence()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        v = out_d[:m].cpu().numpy()         # {x, y, z, rgba bits} records: the colour goes out as its integer value
+        dump_outputs(args.dump_outputs, {"voxel_xyz": v[:, :3], "voxel_rgba": v[:, 3].view(np.uint32).astype(np.float64)})
     if world > 1:
         tmax = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -1059,6 +1103,8 @@ def main():
         d = dense_leg(args, torch, dist, capi, synth, world, rank, local_rank, comm, args.width, args.height, args.steps, args.warmup,
                       want_cpu=(rank == 0 and world == 1 and not args.no_cpu_baseline))
         elapsed = tmax(d["elapsed"])
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, _records([d["res"]], [d["pool"].pairs[d["last_j"]].seed]))
         out = {
             "metric": metric, "value": args.iterations * args.steps / elapsed, "unit": "ICP iterations/s", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True,
@@ -1142,7 +1188,10 @@ def main():
         gather = _HostGather()
     pose_exchange = ("none (1 rank)" if gather is None else "rccl: ncclAllGather behind the C-ABI (slam3d_pose_gather_*)" if comm is not None
                      else "gloo through torch.distributed (tests)" if host_comm else "torch.distributed fallback (slam3d_comm self-test failed)")
-    elapsed, res, table, step_seeds, diag = timed_stream(torch, dist, world, streamer, args.steps, args.warmup, aligns, gather, P)
+    last_step = [] if args.dump_outputs else None
+    elapsed, res, table, step_seeds, diag = timed_stream(torch, dist, world, streamer, args.steps, args.warmup, aligns, gather, P, last_step)
+    if last_step and rank == 0:
+        dump_outputs(args.dump_outputs, _records(last_step[0], last_step[0].seeds))
     elapsed = tmax(elapsed)
     # per-rank attribution of a sub-linear scaling curve: this rank's host-to-device rate with nothing else
     # running (all ranks measure at once: they share the host's PCIe root / memory controllers exactly as in the timed region),

@@ -61,3 +61,25 @@ def test_compact_line_never_exceeds_the_limit():
     full["config3"]["roofline"]["kernel"] = "k" * 3000
     s = bench.compact_line(full, None)
     assert len(s.encode()) < 6000 and all(k in json.loads(s) for k in CONTRACT)
+
+
+def test_dump_outputs_keeps_dtypes_and_a_seeded_sample_under_the_budget(tmp_path, monkeypatch):
+    """--dump-outputs: float32 stays float32, everything else is float64; past the budget every array keeps the same seeded
+    sample of rows from run to run, with the row indices beside it, and the files stay under the budget."""
+    import numpy as np
+    recs = [dict(T=np.eye(4) * (i + 1), T_raw=np.eye(4), norm=0.5 * i, rmse=0.01, inliers=100 + i, status=0, iterations=20,
+                 n_src=300, n_tgt=310) for i in range(3)]
+    a = bench._records(recs, [7, 8, 9])
+    assert a["T"].shape == (3, 4, 4) and a["seed"].tolist() == [7.0, 8.0, 9.0] and a["inliers"].tolist() == [100.0, 101.0, 102.0]
+    bench.dump_outputs(str(tmp_path / "small"), dict(a, pts=np.ones((5, 3), np.float32), lab=np.arange(4, dtype=np.int32)))
+    assert np.load(tmp_path / "small" / "pts.npy").dtype == np.float32 and np.load(tmp_path / "small" / "lab.npy").dtype == np.float64
+    assert np.array_equal(np.load(tmp_path / "small" / "T.npy"), a["T"]) and not list((tmp_path / "small").glob("*_rows.npy"))
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 1 << 16)
+    big = {"pts": np.arange(40000 * 3, dtype=np.float32).reshape(-1, 3), "lab": np.arange(30000, dtype=np.int32)}
+    for d in ("b1", "b2"):
+        bench.dump_outputs(str(tmp_path / d), big)
+    assert sum(f.stat().st_size for f in (tmp_path / "b1").iterdir()) <= (1 << 16) + 4 * 128      # + the .npy headers
+    for k in ("pts", "lab"):
+        rows = np.load(tmp_path / "b1" / f"{k}_rows.npy")
+        assert np.array_equal(rows, np.load(tmp_path / "b2" / f"{k}_rows.npy")) and 0 < rows.size < big[k].shape[0]
+        assert np.array_equal(np.load(tmp_path / "b1" / f"{k}.npy"), big[k][rows.astype(np.int64)])

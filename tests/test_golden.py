@@ -11,7 +11,6 @@ from slam3d_gx_amd import synth
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLD = json.load(open(os.path.join(HERE, "golden", "synthetic_golden.json")))
-REF = "/root/reference"
 
 
 def sha(a):
@@ -79,8 +78,8 @@ def test_hip_path_reproduces_golden(gpu_lib, c):
     _check(c, r["n_src"], r["n_tgt"], r["inliers"], r["status"], r["norm"], Tt[-1], St[-1], idx, d2)
 
 
-# ---------------------------------------------------------------- reference fixtures (only where /root/reference exists)
-needs_ref = pytest.mark.skipif(not os.path.isdir(REF), reason="/root/reference not present (GPU box)")
+# ---------------------------------------------------------------- reference fixtures (committed copies under golden/kinect)
+KINECT = os.path.join(HERE, "golden", "kinect")
 
 
 def _read_png16(path):
@@ -89,8 +88,9 @@ def _read_png16(path):
 
 
 def _read_pcd_xyz(path):
-    """binary PCD v0.7 'x y z rgba' 16-byte records (written by the reference's src/convert2PCD.cpp:72-78)."""
-    raw = open(path, "rb").read()
+    """binary PCD v0.7 'x y z rgba' 16-byte records (written by the reference's src/convert2PCD.cpp:72-78), xz-compressed."""
+    import lzma
+    raw = lzma.open(path).read()
     head_end = raw.index(b"DATA binary\n") + len(b"DATA binary\n")
     header = raw[:head_end].decode("ascii", "replace")
     n = int([l for l in header.splitlines() if l.startswith("POINTS")][0].split()[1])
@@ -99,27 +99,23 @@ def _read_pcd_xyz(path):
     return rec[:, :3]
 
 
-@needs_ref
 @pytest.mark.parametrize("k", [1, 2])
 def test_backprojection_pinned_by_reference_pcd(k):
     """S1 is the one stage a reference artefact pins: data/exp1/pcd/k.pcd was produced by the reference's
     convert2PCD from data/exp1/dep/k.png (raster order, zero depth dropped, src/convert2PCD.cpp:54-72)."""
-    d = _read_png16(os.path.join(REF, f"data/exp1/dep/{k}.png"))
+    d = _read_png16(os.path.join(KINECT, f"exp1_dep_{k}.png"))
     p = O.params(synth.Intrinsics(), z_filter=1e9)          # the PCD has no PassThrough applied
     cloud = O.backproject(d, p).reshape(-1, 4)
     ours = cloud[d.reshape(-1) > 0, :3]
-    ref = _read_pcd_xyz(os.path.join(REF, f"data/exp1/pcd/{k}.pcd"))
+    ref = _read_pcd_xyz(os.path.join(KINECT, f"exp1_pcd_{k}.pcd.xz"))
     assert ours.shape == ref.shape
     assert np.abs(ours - ref).max() <= 1e-6
 
 
-@needs_ref
 def test_oracle_reproduces_reference_golden():
     G = json.load(open(os.path.join(HERE, "golden", "reference_golden.json")))
     intr = synth.Intrinsics()
-    d1 = _read_png16(os.path.join(REF, "data/exp1/dep/1.png"))
-    d2 = _read_png16(os.path.join(REF, "data/exp1/dep/2.png"))
-    db = _read_png16(os.path.join(REF, "bin/dep_1.png"))
+    d1, d2, db = _kinect()
     assert int((d1 > 0).sum()) == G["inputs"]["dep1"]["nonzero"] == 221202
     assert int((d2 > 0).sum()) == G["inputs"]["dep2"]["nonzero"] == 236128
     assert int((db > 0).sum()) == G["inputs"]["bin_dep_1"]["nonzero"] == 201063
@@ -132,9 +128,6 @@ def test_oracle_reproduces_reference_golden():
     c = G["real_pair_dep1_to_dep2"]["0"]
     r = O.icp(c1, c2, O.params(intr, estimator=0, iterations=c["iterations"], nn_method=1))
     _check(c, r["n_src"], r["n_tgt"], r["inliers"], r["status"], r["norm"], r["T_trace"][-1], r["sums_trace"][-1], r["idx"], r["d2"])
-
-
-KINECT = os.path.join(HERE, "golden", "kinect")
 
 
 def _kinect():

@@ -710,7 +710,7 @@ def test_bench_single_gpu_line_has_the_contract_fields(gpu_lib, tmp_path):
     legs = str(tmp_path / "legs.json")
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--width", "320", "--height", "240",
            "--iterations", "6", "--pairs-per-step", "6", "--pool", "4", "--profile-aligns", "4", "--force-collective", "--in-flight", "4",
-           "--legs-file", legs]
+           "--legs-file", legs, "--dump-outputs", str(tmp_path / "dump")]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=root)
     assert out.returncode == 0, out.stdout[-1500:] + out.stderr[-1500:]
     last = out.stdout.rstrip("\n").splitlines()[-1]
@@ -727,6 +727,13 @@ def test_bench_single_gpu_line_has_the_contract_fields(gpu_lib, tmp_path):
     assert d["config"]["gathered_pose_records"] == 6 and "workload" in d["config"]
     assert d["rccl_ranks"] == 1 and d["pose_exchange"].startswith("rccl")
     assert d["config"]["coarse_iterations"] == 3 and d["config"]["noise_sigma_over_z2"] == 0.0012 and d["config"]["hole_block_px"] == 8
+    # --dump-outputs: the last timed step's six pose records as the caller received them, the first one equal to the oracle's
+    dump = {k: np.load(tmp_path / "dump" / f"{k}.npy") for k in ("T", "T_raw", "norm", "rmse", "inliers", "status", "iterations", "n_src", "n_tgt", "seed")}
+    assert all(a.dtype == np.float64 and a.shape[0] == 6 for a in dump.values()) and dump["T"].shape == (6, 4, 4)
+    assert (dump["status"] == 0).all() and ((dump["iterations"] >= 1) & (dump["iterations"] <= 6)).all() and len(set(dump["seed"].tolist())) == 6
+    pr, s4, t4 = _pair(int(dump["seed"][0]), 320, 240, noise_sigma=0.0012, hole_block=8, hole_prob=0.25)
+    ro = O.icp(s4, t4, O.params(pr.intr, iterations=6, nn_method=1))
+    assert np.array_equal(dump["T_raw"][0], ro["T_trace"][-1]) and dump["inliers"][0] == ro["inliers"]
     # the roofline's algorithmic bytes count the three coarse launches of the six at a quarter of the sources
     assert d["roofline"]["algorithmic_bytes_per_launch"] < 16 * 0.7 * 76800 + 24 * 76800
     # the complete object: same headline, plus what the line leaves out
@@ -969,18 +976,19 @@ def test_config5_dense_1280x960_eight_emulated_ranks(gpu_lib):
     assert np.array_equal(merged, idx_whole) and np.array_equal(merged, ro["idx"])
 
 
-def test_config4_shape_eight_ranks_of_64_pairs_on_one_device(gpu_lib, tmp_path):
-    """BASELINE config 4's shape: 512 frame pairs of 640x480 (seeds 1000..1511) sharded over EIGHT ranks,
-    64 per rank in one launch sequence, the step's 512 pose records gathered on every rank -- eight processes on this one
-    GPU over gloo (RCCL needs a GPU per rank; everything else is the code the driver's 8-GPU run executes), started the way
-    the driver starts it: a plain `python bench.py --gpus 8 ...`.  The gathered table must be in pair order (rank r holds
-    the contiguous block of seeds 1000 + 64 r ...) and sampled pairs bit-identical to the oracle."""
+def test_config4_shape_four_ranks_of_128_pairs_on_one_device(gpu_lib, tmp_path):
+    """BASELINE config 4's step: 512 frame pairs of 640x480 (seeds 1000..1511) sharded over the ranks in
+    launches of 64 pairs, the step's 512 pose records gathered on every rank -- here FOUR processes on this one GPU over gloo
+    (128 pairs, two launches of 64 per rank and step; RCCL needs a GPU per rank, and four ranks plus this process keep the
+    count of processes holding the GPU at five; everything else is the code the driver's 8-GPU run executes), started the
+    way the driver starts it: a plain `python bench.py --gpus N ...`.  The gathered table must be in pair order (rank r holds
+    the contiguous block of seeds 1000 + 128 r ...) and sampled pairs bit-identical to the oracle."""
     import json, os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     dump = str(tmp_path / "table.json")
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--steps", "1", "--warmup", "1", "--pairs", "64",
-           "--pairs-per-step", "64", "--pool", "64", "--in-flight", "1", "--no-cpu-baseline", "--no-bruteforce", "--profile-aligns", "1",
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "4", "--steps", "1", "--warmup", "1", "--pairs", "64",
+           "--pairs-per-step", "128", "--pool", "128", "--in-flight", "1", "--no-cpu-baseline", "--no-bruteforce", "--profile-aligns", "1",
            "--overlap-aligns", "0", "--dist-backend", "gloo", "--one-device", "--dump-table", dump, "--legs-file", str(tmp_path / "legs.json")]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=2400, cwd=root, env=env)
     assert out.returncode == 0, out.stdout[-1500:] + out.stderr[-3000:]
@@ -988,15 +996,15 @@ def test_config4_shape_eight_ranks_of_64_pairs_on_one_device(gpu_lib, tmp_path):
     assert len(last.encode()) < 6000
     d = json.loads(last)
     d["per_rank"] = json.load(open(tmp_path / "legs.json"))["per_rank"]
-    assert d["n_gpus"] == 8 and d["value"] > 0 and d["scaling"] == "weak" and d["survey_8d"]["gpus"] == 8
+    assert d["n_gpus"] == 4 and d["value"] > 0 and d["scaling"] == "weak" and d["survey_8d"]["gpus"] == 4
     assert d["config"]["gathered_pose_records"] == 512 and d["config"]["pairs_per_launch"] == 64
     assert d["config"]["coarse_iterations"] == 3 and d["config"]["synthetic_workload"].startswith("BASELINE.md section 4")
-    assert [r["rank"] for r in d["per_rank"]] == list(range(8)) and all(r["h2d_GBps"] > 0 and r["enqueue_us_per_alignment"] > 0 and r["gather_us_per_step"] > 0 for r in d["per_rank"])
+    assert [r["rank"] for r in d["per_rank"]] == list(range(4)) and all(r["h2d_GBps"] > 0 and r["enqueue_us_per_alignment"] > 0 and r["gather_us_per_step"] > 0 for r in d["per_rank"])
     assert d["config"]["gathered_seeds"] == {"first": [1000, 1001], "last": [1510, 1511], "ascending": True}
     tab = json.load(open(dump))
-    assert tab["seeds"] == list(range(1000, 1512)) and tab["world"] == 8 and tab["pairs_per_rank"] == 64
+    assert tab["seeds"] == list(range(1000, 1512)) and tab["world"] == 4 and tab["pairs_per_rank"] == 128
     assert all(s == 0 for s in tab["status"]), [i for i, s in enumerate(tab["status"]) if s][:8]
-    for k in (0, 63, 64, 200, 383, 511):                          # both ends of rank blocks and interior pairs
+    for k in (0, 63, 64, 127, 128, 200, 383, 384, 511):           # both ends of rank blocks and of launches, and interior pairs
         pr, s4, t4 = _pair(1000 + k, 640, 480, noise_sigma=0.0012, hole_block=8, hole_prob=0.25)      # bench.py's default workload: BASELINE.md section 4's
         ro = O.icp(s4, t4, O.params(pr.intr, iterations=20, nn_method=1))
         assert np.array_equal(np.array(tab["T"][k]).reshape(4, 4), ro["T_trace"][-1]), k

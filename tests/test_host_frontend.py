@@ -83,7 +83,7 @@ def _pcd_checksum(rec):
 
 def test_pcd_reader_writer(tmp_path):
     """Row f-1: PCD v0.7 binary (the reference's format, src/convert2PCD.cpp:75-79) and ascii, incl. the reference's
-    own data/exp1/pcd/1.pcd when it is present (221,202 records, 3,911 trailing bytes ignored)."""
+    own data/exp1/pcd/1.pcd (committed under tests/golden/kinect; 221,202 records, 3,911 trailing bytes ignored)."""
     _build_host()
     exe = os.path.join(HOST, "host_selftest")
     rng = np.random.default_rng(4)
@@ -110,14 +110,15 @@ def test_pcd_reader_writer(tmp_path):
     assert subprocess.run([exe, "pcd", str(tmp_path / "nope.pcd"), str(tmp_path / "x.pcd")], capture_output=True).returncode == 1
     (tmp_path / "e.pcd").write_text("hello\n")
     assert subprocess.run([exe, "pcd", str(tmp_path / "e.pcd"), str(tmp_path / "x.pcd")], capture_output=True).returncode == 1
-    ref = "/root/reference/data/exp1/pcd/1.pcd"
-    if os.path.exists(ref):
-        raw = open(ref, "rb").read()
-        k = raw.index(b"DATA binary\n") + 12
-        body = np.frombuffer(raw, dtype=np.float32, count=4 * 221202, offset=k).reshape(-1, 4)
-        out = subprocess.run([exe, "pcd", ref, str(tmp_path / "r.pcd")], capture_output=True, text=True)
-        assert out.stdout.split() == ["pcd", "221202", "221202", "1", str(_pcd_checksum(body))]
-        assert (tmp_path / "r.pcd").read_bytes() == raw[: k + 16 * 221202]                # same header, same records
+    import lzma
+    raw = lzma.open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "kinect", "exp1_pcd_1.pcd.xz")).read()
+    ref = tmp_path / "ref.pcd"
+    ref.write_bytes(raw)
+    k = raw.index(b"DATA binary\n") + 12
+    body = np.frombuffer(raw, dtype=np.float32, count=4 * 221202, offset=k).reshape(-1, 4)
+    out = subprocess.run([exe, "pcd", str(ref), str(tmp_path / "r.pcd")], capture_output=True, text=True)
+    assert out.stdout.split() == ["pcd", "221202", "221202", "1", str(_pcd_checksum(body))]
+    assert (tmp_path / "r.pcd").read_bytes() == raw[: k + 16 * 221202]                # same header, same records
 
 
 def test_generate_trajectory_tool(tmp_path):

@@ -167,7 +167,7 @@ def test_pose_error_matches_the_reference_tool():
     """Row a14, pinned by the reference itself: orc_pose_error (the metric every parity test and bench leg reports) against the
     numbers the reference's tools/evaluate_rpe.py functions (ominus, compute_angle, compute_distance) returned for 96 seeded
     pose pairs -- tests/golden/pose_error_golden.json, made by tests/golden/make_pose_error_golden.py, which executes those
-    functions where they lie under /root/reference.  The two differ only in how the relative pose is formed (numpy.linalg.inv
+    functions where they lie in the reference repository.  The two differ only in how the relative pose is formed (numpy.linalg.inv
     there, the analytic inverse here): 1e-9 on the angle away from 0, 5e-8 where acos meets a trace rounded next to 3."""
     import json, os
     g = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "pose_error_golden.json")))

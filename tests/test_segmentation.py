@@ -15,7 +15,7 @@ import oracle_lib as O
 from slam3d_gx_amd import synth
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-REF = "/root/reference"
+KINECT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "kinect")
 G = json.load(open(os.path.join(HERE, "golden", "segmentation_golden.json")))
 
 
@@ -45,10 +45,9 @@ def test_oracle_reproduces_segmentation_golden(c):
     _check(c, *O.segment_planes(s4, seed=c["seed"]))
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference fixtures not present")
 def test_oracle_segmentation_on_reference_frame():
     from PIL import Image
-    d = np.array(Image.open(os.path.join(REF, "data/exp1/dep/1.png"))).astype(np.uint16)
+    d = np.array(Image.open(os.path.join(KINECT, "exp1_dep_1.png"))).astype(np.uint16)
     c1 = O.backproject(d, O.params(synth.Intrinsics()))
     planes, labels = O.segment_planes(c1, seed=1)
     _check(G["reference_dep1"], planes, labels)

@@ -1,8 +1,8 @@
 """f-1: PassThrough + VoxelGrid of GraphicEnd::readimage (src/GraphicEnd.cpp:283-295).
 
 PCL is not in the tree, so parity is UNPINNED; the oracle (oracle/voxel_oracle.c) is checked here against an
-independent numpy restatement of the same published algorithm, against golden vectors, and -- when the
-reference is present -- on its own data/exp1/pcd/{1,2}.pcd at its own operating point (221,202 -> ~16 k points,
+independent numpy restatement of the same published algorithm, against golden vectors, and on the
+reference's own data/exp1/pcd/{1,2}.pcd (committed copies, tests/golden/kinect) at its own operating point (221,202 -> ~16 k points,
 SURVEY.md row a4).  The HIP path must give the oracle's bits for any input order.
 """
 import hashlib
@@ -16,7 +16,6 @@ import oracle_lib as O
 from slam3d_gx_amd import synth
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-REF = "/root/reference"
 G = json.load(open(os.path.join(HERE, "golden", "voxel_golden.json")))
 
 
@@ -98,14 +97,17 @@ def test_voxel_semantics_and_edge_cases():
     assert np.unique(ijk, axis=0).shape[0] >= 0.999 * a.shape[0]      # centroids may round across a face: rare
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference fixtures not present")
 @pytest.mark.parametrize("k", [1, 2])
-def test_oracle_on_reference_pcd_operating_point(k):
-    """The reference's own frames at its own settings (grid_leaf 0.03, z_filter 7.0, parameters.yaml:41,65)."""
+def test_oracle_on_reference_pcd_operating_point(k, tmp_path):
+    """The reference's own frames at its own settings (grid_leaf 0.03, z_filter 7.0, parameters.yaml:41,65), from the
+    committed copies of its data/exp1/pcd/{1,2}.pcd (golden/kinect, xz-compressed)."""
+    import lzma
     import sys
     sys.path.insert(0, os.path.join(HERE, "golden"))
     from make_golden import read_pcd16
-    p = read_pcd16(os.path.join(REF, f"data/exp1/pcd/{k}.pcd"))
+    pcd = tmp_path / f"{k}.pcd"
+    pcd.write_bytes(lzma.open(os.path.join(HERE, "golden", "kinect", f"exp1_pcd_{k}.pcd.xz")).read())
+    p = read_pcd16(str(pcd))
     g = G[f"reference_pcd{k}"]
     assert p.shape[0] == g["points"] == (221202, 236128)[k - 1]
     v = O.voxel_grid(p, 0.03, 7.0)
