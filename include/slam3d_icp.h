@@ -46,12 +46,15 @@ enum {
     SLAM3D_E_COMM = -6              /* RCCL error / librccl not loadable (see slam3d_comm_last_error) */
 };
 
-/* Estimators.  POINT2PLANE: target normals from the 7x7 organized window (src/planarFeatures.cpp:88-136); SVD: point-to-point
+/* Estimators.  POINT2PLANE: target normals from the 7x7 organized window (src/planarFeatures.cpp:88-136) -- on a point list (height == 1)
+ * from the metric ball of slam3d_icp_set_list_normal_params instead (DESIGN.md spec S2l, pcl::NormalEstimation with a radius search);
+ * SVD: point-to-point
  * (Kabsch).  PLANE (ABI 6, DESIGN.md spec S2p / S4p): plane-ICP proper -- the target frame's PLANES give the normals.  The frame is
  * segmented on the device exactly as slam3d_segment_planes does (the pcl::SACSegmentation loop of src/GraphicEnd.cpp:353-430, with
  * the parameters of slam3d_icp_set_seg_params), every pixel labelled with plane r takes the plane's least-squares normal
  * (a, b, c) (the fit of src/GraphicEnd.cpp:360-375, d >= 0 :383-387: toward the camera) -- SURVEY.md App. C2 "points take their
- * plane's normal" --, a pixel on no plane keeps its 7x7-window normal (or is no target at all with SLAM3D_PLANE_ONLY); rows,
+ * plane's normal" --, a pixel on no plane keeps its 7x7-window normal (a point of a list: its ball normal; or is no target at all with
+ * SLAM3D_PLANE_ONLY); rows,
  * search, solve and result are those of POINT2PLANE.  Role in the reference: planes are extracted per frame and the pose is
  * derived from plane-wise correspondences, src/GraphicEnd.cpp:158,168,557-659. */
 enum { SLAM3D_EST_POINT2PLANE = 0, SLAM3D_EST_SVD = 1, SLAM3D_EST_PLANE = 2 };
@@ -81,7 +84,7 @@ typedef struct slam3d_icp_params {
     int32_t iterations;             /* icp_iterations (20); fixed count, no early exit               */
     double  max_corr_dist;          /* icp_max_corr_dist (0.10 m)                                    */
     int32_t estimator;              /* SLAM3D_EST_*                                                  */
-    int32_t normal_window;          /* 7   (src/planarFeatures.cpp:92)                               */
+    int32_t normal_window;          /* 7   (src/planarFeatures.cpp:92); 0 = no image window (point lists, spec S2l) */
     int32_t normal_min_inliers;     /* 41  (src/planarFeatures.cpp:128, "> 40")                      */
     double  normal_inlier_dist;     /* 0.01 (src/planarFeatures.cpp:123)                             */
     int32_t min_inliers;            /* 12  (multiPnP default, src/GraphicEnd.h:134)                  */
@@ -109,7 +112,13 @@ typedef struct slam3d_icp_params {
  * produces (PCD -> PassThrough -> VoxelGrid: 16,034 / 14,758 points for the reference's data/exp1 frames, src/GraphicEnd.cpp:283-295)
  * and hands to the plane extraction (:158).  Views may then carry any width <= params.width (height 1); records beyond a view are
  * invalid.  No camera model is assumed (fx .. cy unused; |x|, |y| <= z for the range check), there are no image windows or tiles:
- * the estimator is SLAM3D_EST_SVD or SLAM3D_EST_PLANE with SLAM3D_PLANE_ONLY (SLAM3D_E_INVALID otherwise) and SLAM3D_NN_AUTO selects
+ * SLAM3D_EST_SVD and SLAM3D_EST_PLANE with SLAM3D_PLANE_ONLY need no normals and take any normal_window.  SLAM3D_EST_POINT2PLANE and
+ * SLAM3D_EST_PLANE without SLAM3D_PLANE_ONLY (any pair gate) need a normal per point: a list has no image window, so they require
+ * normal_window = 0 -- "no window" -- and are refused with a window (SLAM3D_E_INVALID, as before ABI 8 gained list normals without a
+ * version bump: entry points were added, no struct changed).  A point's normal (POINT2PLANE, and PLANE's fallback for points on no plane)
+ * then comes from its metric ball, spec S2l -- the valid points of the same list within `radius` (slam3d_icp_set_list_normal_params;
+ * normal_min_inliers / normal_inlier_dist are not used), with every valid point within 16 m of the sensor (3 z_filter^2 < 256,
+ * SLAM3D_E_INVALID otherwise).  SLAM3D_NN_AUTO selects
  * one persistent launch per run (round 6: Morton-cell tiles, exact tile-pruned search; SLAM3D_NN_MFMA16 / _MFMA / _VALU keep the full scans).
  * Spec S4c's coarse iterations take the points whose index i satisfies (i / 8) mod 4 == 0.  The persistent launch needs all its blocks
  * resident (at most four such runs in flight per device and process): should a grid barrier not open within
@@ -352,6 +361,23 @@ int slam3d_icp_set_seg_params(slam3d_icp_handle *h, const slam3d_seg_params *sp)
 int slam3d_icp_get_frame_planes(slam3d_icp_handle *h, int32_t frame, slam3d_plane *planes /* 8 */, int32_t *nplanes);
 /* the association the pair gate of the LAST run used for pair `slot`: assoc[i] = target plane of source plane i, or -1; 8 entries */
 int slam3d_icp_get_plane_assoc(slam3d_icp_handle *h, int32_t slot, int32_t *assoc /* 8 */);
+
+/* ---- point-list normals (DESIGN.md spec S2l; ABI 8, added without a version bump) ----------------------------------------
+ * The normal of a point of a list (height == 1 handle, SLAM3D_EST_POINT2PLANE or SLAM3D_EST_PLANE without SLAM3D_PLANE_ONLY) is spec S2
+ * on its ball N(i) = { valid j of the same list : fmaf(dz,dz,fmaf(dy,dy,dx*dx)) <= (float)(radius^2) } instead of a 7x7 window:
+ * no normal when |N(i)| < min_points or |N(i)| > 2048, else the eigenvector of the smallest eigenvalue of the integer moments, toward
+ * the camera, planar (a target) when at least min_inliers members lie within inlier_dist of its plane.  Order-free: shuffling a list
+ * moves the normals with their points and changes no bit. */
+typedef struct slam3d_list_normal_params {
+    float   radius;                 /* metres, (0, 0.45]: the bound that keeps the ball's moments exact        */
+    int32_t min_points;             /* [3, 2048]                                                                               */
+    int32_t min_inliers;            /* [1, 2048]                                                                               */
+    float   inlier_dist;            /* metres, (0, 1]                                                                          */
+} slam3d_list_normal_params;
+void slam3d_list_normal_default_params(slam3d_list_normal_params *lp);
+/* SLAM3D_E_STATE on an organized handle (its normals are S2's windows), SLAM3D_E_INVALID out of range.
+ * Every frame's normals and target list are rebuilt at the next run. */
+int slam3d_icp_set_list_normal_params(slam3d_icp_handle *h, const slam3d_list_normal_params *lp);
 
 /* ---- dense (single pair sharded over ranks) building blocks, one exchange per iteration -- */
 /* restrict the source rows this handle works on to [row_begin,row_end) of slot 0 */

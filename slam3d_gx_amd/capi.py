@@ -38,6 +38,7 @@ EXPORTED_SYMBOLS = [
     "slam3d_pose_gather_collect", "slam3d_pose_gather", "slam3d_pose_record_from_result",
     "slam3d_plane_gate", "slam3d_device_count",
     "slam3d_icp_set_seg_params", "slam3d_icp_get_frame_planes", "slam3d_icp_get_plane_assoc", "slam3d_voxel_grid_batch_device", "slam3d_icp_dense_run_with", "slam3d_icp_set_fault_injection", "slam3d_voxel_grid_path_counts",
+    "slam3d_list_normal_default_params", "slam3d_icp_set_list_normal_params",
 ]
 COMM_ID_BYTES = 128
 
@@ -87,6 +88,21 @@ class SegParams(C.Structure):
                 ("hypotheses", C.c_int32), ("seed", C.c_uint64)]
 
 
+class ListNormalParams(C.Structure):      # slam3d_list_normal_params (spec S2l)
+    _fields_ = [("radius", C.c_float), ("min_points", C.c_int32), ("min_inliers", C.c_int32), ("inlier_dist", C.c_float)]
+
+
+def list_normal_params(**kw) -> ListNormalParams:
+    """slam3d_list_normal_default_params, then the given fields"""
+    lp = ListNormalParams()
+    load_library().slam3d_list_normal_default_params(C.byref(lp))
+    for k, v in kw.items():
+        if not hasattr(lp, k):
+            raise AttributeError(k)
+        setattr(lp, k, v)
+    return lp
+
+
 class Slam3dError(RuntimeError):
     def __init__(self, code: int, msg: str):
         super().__init__(f"slam3d_icp error {code}: {msg}")
@@ -113,7 +129,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.slam3d_icp_create.argtypes = [C.POINTER(Params), C.POINTER(C.c_void_p)]
     lib.slam3d_icp_destroy.argtypes = [C.c_void_p]
     lib.slam3d_icp_destroy.restype = None
-    void_fns = ("slam3d_icp_destroy", "slam3d_icp_default_params", "slam3d_seg_default_params", "slam3d_comm_destroy",
+    void_fns = ("slam3d_icp_destroy", "slam3d_icp_default_params", "slam3d_seg_default_params", "slam3d_list_normal_default_params", "slam3d_comm_destroy",
                 "slam3d_shard_range", "slam3d_pose_record_from_result")
     for name in EXPORTED_SYMBOLS:
         fn = getattr(lib, name)
@@ -488,6 +504,16 @@ class IcpHandle:
     # ---- SLAM3D_EST_PLANE ----------------------------------------------------------------
     def set_seg_params(self, sp: SegParams):
         self._check(self.lib.slam3d_icp_set_seg_params(self._h, C.byref(sp)), False)
+
+    # ---- point-list normals (spec S2l) --------------------------------------------------------
+    def set_list_normal_params(self, lp: Optional[ListNormalParams] = None, **kw):
+        """the ball of a list point's normal; kw: fields over the defaults (or over lp)"""
+        lp = lp or list_normal_params()
+        for k, v in kw.items():
+            if not hasattr(lp, k):
+                raise AttributeError(k)
+            setattr(lp, k, v)
+        self._check(self.lib.slam3d_icp_set_list_normal_params(self._h, C.byref(lp)), False)
 
     def get_frame_planes(self, frame: int) -> list:
         planes = (Plane * 8)()

@@ -127,6 +127,12 @@ struct slam3d_icp_handle {
     int *ls_n = nullptr;                            // [maxF][2][2]: points, tiles
     int *ls_cnt = nullptr, *ls_cstart = nullptr, *ls_grp = nullptr; int2 *ls_cr = nullptr, *ls_super = nullptr;
     float4 *ls_match = nullptr;                     // [maxB][ls_npad]: previous match (point, index) by sorted source position
+    // point-list normals (spec S2l, k_list_normals): on with POINT2PLANE, or PLANE without SLAM3D_PLANE_ONLY, on a height == 1 handle.
+    // The frame is sorted in a third role, NORMALS, into LS_TASKS scratch lists (the counting sort's scratch above is shared)
+    bool list_nrm = false;
+    slam3d_list_normal_params lnp;                  // slam3d_icp_set_list_normal_params
+    float4 *ln_pts = nullptr, *ln_box = nullptr;    // [LS_TASKS][ls_npad], [LS_TASKS][ls_ntile * 2]
+    int2 *ln_tile = nullptr; int *ln_n = nullptr;   // [LS_TASKS][ls_ntile], [LS_TASKS][2]
     long long *ls_dbg = nullptr;                    // SLAM3D_LIST_DEBUG=1: block 0's per-iteration stamps (slam3d_icp_get_nn_debug)
     int dense_fail_at = -1;       // slam3d_icp_set_fault_injection (tests): the dense loop's iteration that "cannot be enqueued" on this handle
     hipGraphExec_t graph_exec = nullptr;   // the captured iteration loop (slam3d_icp_run without profiling)
@@ -274,6 +280,7 @@ static void free_all(slam3d_icp_handle *h)
     auto F = [](auto *&p) { if (p) { (void)hipFree(p); p = nullptr; } };
     F(h->f_cloud); F(h->f_nrm); F(h->f_srcT); F(h->f_tgtT); F(h->f_tbox); F(h->f_cbox); F(h->f_tq); F(h->f_scount); F(h->f_counts);
     F(h->seg_scratch); F(h->ls_dbg); F(h->ls_pts); F(h->ls_box); F(h->ls_tile); F(h->ls_super); F(h->ls_n); F(h->ls_cnt); F(h->ls_cstart); F(h->ls_grp); F(h->ls_cr); F(h->ls_match);
+    F(h->ln_pts); F(h->ln_box); F(h->ln_tile); F(h->ln_n);
     F(h->src_c); F(h->tgt_c); F(h->ccounts); F(h->chunk_cnt); F(h->corr); F(h->ticket);
     F(h->flags); F(h->best); F(h->cd2); F(h->acc); F(h->sums); F(h->Tcur); F(h->trace_T); F(h->trace_S);
     F(h->d_pairs); F(h->d_raw); F(h->d_depth); F(h->d_idx); F(h->d_d2); F(h->d_scratch4); F(h->corr_trace);
@@ -313,13 +320,18 @@ extern "C" int slam3d_icp_create(const slam3d_icp_params *p, slam3d_icp_handle *
     if (!p || !out) return SLAM3D_E_INVALID;
     *out = nullptr;
     if (p->width <= 0 || p->height <= 0 || p->max_batch <= 0 || p->iterations < 0 || p->extra_frames < 0 || p->coarse_iterations < 0) return SLAM3D_E_INVALID;
-    if (p->normal_window < 1 || (p->normal_window & 1) == 0 || p->normal_window / 2 > NRM_RMAX) return SLAM3D_E_INVALID;
+    const bool unorganized = p->height == 1 && p->width > 1;
+    // normal_window 0 = no image window: only a point list (height == 1) may say so -- its normals then come from metric balls (spec S2l)
+    if (!(unorganized && p->normal_window == 0) && (p->normal_window < 1 || (p->normal_window & 1) == 0 || p->normal_window / 2 > NRM_RMAX))
+        return SLAM3D_E_INVALID;
     if (p->estimator != SLAM3D_EST_POINT2PLANE && p->estimator != SLAM3D_EST_SVD && p->estimator != SLAM3D_EST_PLANE) return SLAM3D_E_INVALID;
     if (p->plane_flags & ~(SLAM3D_PLANE_PAIR_GATE | SLAM3D_PLANE_ONLY)) return SLAM3D_E_INVALID;
     if (p->plane_flags != 0 && p->estimator != SLAM3D_EST_PLANE) return SLAM3D_E_INVALID;
-    // unorganized clouds (height == 1) have no 7x7 image windows: svd, or the planes alone
-    if (p->height == 1 && p->width > 1 && (p->estimator == SLAM3D_EST_POINT2PLANE || (p->estimator == SLAM3D_EST_PLANE && !(p->plane_flags & SLAM3D_PLANE_ONLY))))
-        return SLAM3D_E_INVALID;
+    // unorganized clouds (height == 1) have no image windows: a list estimator that needs normals is refused unless the parameters say
+    // so (normal_window = 0); the normals then come from metric balls (spec S2l, k_list_normals)
+    const bool list_nrm = unorganized &&
+                          (p->estimator == SLAM3D_EST_POINT2PLANE || (p->estimator == SLAM3D_EST_PLANE && !(p->plane_flags & SLAM3D_PLANE_ONLY)));
+    if (list_nrm && p->normal_window != 0) return SLAM3D_E_INVALID;
     if (p->nn_mode < SLAM3D_NN_AUTO || p->nn_mode > SLAM3D_NN_TILES) return SLAM3D_E_INVALID;
     if (!(p->max_corr_dist > 0.0) || !(p->z_filter > 0.0)) return SLAM3D_E_INVALID;
     {   // range of the int64 fixed-point sums (unit 2^-32): a term is at most |p|^2, all N slots may carry one.  With the
@@ -338,7 +350,10 @@ extern "C" int slam3d_icp_create(const slam3d_icp_params *p, slam3d_icp_handle *
             return SLAM3D_E_INVALID;
         // spec S2: the window moments C' = n S2 - S1 S1^T must be exact integers below 2^53: n^2 (r 2^16)^2 < 2^53 with n = window^2
         // (7x7 at z_filter 7 m: 11 times below; a 9x9 window beyond ~17 m is refused, not computed inexactly -- ADVICE r4)
-        if (p->estimator != SLAM3D_EST_SVD) {
+        // spec S2l: a ball's moments are sums of at most LN_NMAX quantised points; |Xq| < 2^20 (every valid point within 16 m) keeps
+        // n S2 and S1 S1^T below 2^62 in int64 (the radius bound of slam3d_icp_set_list_normal_params keeps their difference below 2^53)
+        if (list_nrm && !(r2 < 256.0)) return SLAM3D_E_INVALID;
+        if (p->estimator != SLAM3D_EST_SVD && !list_nrm) {
             const double nw = (double)p->normal_window * p->normal_window;
             if (!(nw * nw * r2 * 4294967296.0 < 9007199254740992.0)) return SLAM3D_E_INVALID;
         }
@@ -420,14 +435,24 @@ extern "C" int slam3d_icp_create(const slam3d_icp_params *p, slam3d_icp_handle *
     }
     // point lists: one persistent launch per run (list_icp.hpp); SLAM3D_LIST_ICP=0 (developer knob) keeps round 5's three launches per iteration
     h->list_on = p->height == 1 && p->width > 1 && p->nn_mode == SLAM3D_NN_AUTO && !(getenv("SLAM3D_LIST_ICP") && atoi(getenv("SLAM3D_LIST_ICP")) == 0);
-    if (h->list_on) {
+    h->list_nrm = list_nrm;
+    slam3d_list_normal_default_params(&h->lnp);
+    if (h->list_on || h->list_nrm) {
         h->ls_ntile = h->N / 64 + 1 + std::min(h->N, LS_NSUPER);       // tiles never leave a super-cell: at most one partial tile per non-empty super-cell
         h->ls_npad = (h->N + 63) / 64 * 64 + 64;                       // + the padding behind the list
-        A(dalloc(h->ls_pts, F * 2 * h->ls_npad)); A(dalloc(h->ls_box, F * 2 * h->ls_ntile * 2)); A(dalloc(h->ls_tile, F * 2 * h->ls_ntile));
-        A(dalloc(h->ls_n, F * 4)); A(dalloc(h->ls_super, (size_t)LS_TASKS * LS_NSUPER));
-        if (getenv("SLAM3D_LIST_DEBUG")) A(dalloc(h->ls_dbg, (size_t)iters * LS_MAX_BLOCKS * 12));
+        A(dalloc(h->ls_super, (size_t)LS_TASKS * LS_NSUPER));
         A(dalloc(h->ls_cnt, (size_t)LS_TASKS * LS_NCELL)); A(dalloc(h->ls_cstart, (size_t)LS_TASKS * LS_NCELL)); A(dalloc(h->ls_grp, (size_t)LS_TASKS * LS_NGROUP));
-        A(dalloc(h->ls_cr, (size_t)LS_TASKS * h->N)); A(dalloc(h->ls_match, (size_t)h->maxB * h->ls_npad));
+        A(dalloc(h->ls_cr, (size_t)LS_TASKS * h->N));
+    }
+    if (h->list_on) {
+        A(dalloc(h->ls_pts, F * 2 * h->ls_npad)); A(dalloc(h->ls_box, F * 2 * h->ls_ntile * 2)); A(dalloc(h->ls_tile, F * 2 * h->ls_ntile));
+        A(dalloc(h->ls_n, F * 4));
+        if (getenv("SLAM3D_LIST_DEBUG")) A(dalloc(h->ls_dbg, (size_t)iters * LS_MAX_BLOCKS * 12));
+        A(dalloc(h->ls_match, (size_t)h->maxB * h->ls_npad));
+    }
+    if (h->list_nrm) {
+        A(dalloc(h->ln_pts, (size_t)LS_TASKS * h->ls_npad)); A(dalloc(h->ln_box, (size_t)LS_TASKS * h->ls_ntile * 2));
+        A(dalloc(h->ln_tile, (size_t)LS_TASKS * h->ls_ntile)); A(dalloc(h->ln_n, (size_t)LS_TASKS * 2));
     }
     A(dalloc(h->ccounts, (size_t)h->maxB * 4)); A(dalloc(h->ticket, (size_t)h->maxB * 2));      // [maxB, 2 maxB): the list kernel's claim counters
     A(dalloc(h->corr, BS)); A(dalloc(h->flags, (size_t)h->maxB)); A(dalloc(h->cd2, BS));
@@ -504,11 +529,12 @@ extern "C" int slam3d_icp_create(const slam3d_icp_params *p, slam3d_icp_handle *
         }
     }
     (void)hipMemsetAsync(h->ticket, 0, sizeof(unsigned int) * (size_t)h->maxB * 2, h->stream);
-    if (h->list_on) {      // the counting sort's counters clean up after themselves from here on
+    if (h->list_on || h->list_nrm) {      // the counting sort's counters clean up after themselves from here on
         (void)hipMemsetAsync(h->ls_cnt, 0, sizeof(int) * (size_t)LS_TASKS * LS_NCELL, h->stream);
         (void)hipMemsetAsync(h->ls_grp, 0, sizeof(int) * (size_t)LS_TASKS * LS_NGROUP, h->stream);
-        (void)hipMemsetAsync(h->ls_n, 0, sizeof(int) * 4 * F, h->stream);
     }
+    if (h->list_on) (void)hipMemsetAsync(h->ls_n, 0, sizeof(int) * 4 * F, h->stream);
+    if (h->list_nrm) (void)hipMemsetAsync(h->ln_n, 0, sizeof(int) * 2 * LS_TASKS, h->stream);
     h->frames.assign(h->maxF, FrameHost());
     h->pair_src.assign(h->maxB, -1); h->pair_tgt.assign(h->maxB, -1);
     h->h_pairs.assign(h->maxB, PairPtrs{}); h->up_pairs.assign(h->maxB, PairPtrs{});
@@ -898,7 +924,30 @@ static int enqueue_preprocess(slam3d_icp_handle *h, int B, const double *T_init,
     const bool plane_only = is_plane(h) && (h->p.plane_flags & SLAM3D_PLANE_ONLY);
     std::vector<FrameTask> wtasks;                 // the normals tasks that need the 7x7-window pass
     for (size_t k = 0; k < ntasks.size(); ++k) if (nfull[k] && !plane_only) wtasks.push_back(ntasks[k]);
-    for (size_t k0 = 0; k0 < wtasks.size(); k0 += FRAME_ARGS) {
+    for (size_t k0 = 0; k0 < wtasks.size() && h->list_nrm; k0 += LS_TASKS) {
+        // spec S2l: point lists take their normals from metric balls -- each frame sorted in the NORMALS role into scratch list k
+        // (every valid point), then k_list_normals writes every record of the frame (zeros first: invalid records, no normal)
+        ListTasks a; ListNrmOut o;
+        const int n = (int)std::min<size_t>(LS_TASKS, wtasks.size() - k0);
+        for (int k = 0; k < n; ++k) {
+            ListTask &t = a.t[k];
+            t.cloud = wtasks[k0 + k].cloud; t.nrm = nullptr;
+            t.pts = h->ln_pts + (size_t)k * h->ls_npad; t.box = h->ln_box + (size_t)k * h->ls_ntile * 2;
+            t.tile = h->ln_tile + (size_t)k * h->ls_ntile; t.n = h->ln_n + (size_t)k * 2;
+            t.which = 2; t.use_normals = 0; t.i_begin = 0; t.i_end = h->N;
+            o.out[k] = wtasks[k0 + k].nrm;
+            HIPCHK(h, hipMemsetAsync(o.out[k], 0, sizeof(float4) * (size_t)h->N, s));
+        }
+        const dim3 pg((h->N + 255) / 256, n);
+        hipLaunchKernelGGL(k_list_bin, pg, dim3(256), 0, s, a, h->ls_cnt, h->ls_grp, h->ls_cr, h->N, g.zmax);
+        hipLaunchKernelGGL(k_list_scan, dim3(LS_NGROUP, n), dim3(64), 0, s, a, h->ls_cnt, h->ls_cstart, h->ls_grp, h->ls_super);
+        hipLaunchKernelGGL(k_list_scatter, pg, dim3(256), 0, s, a, h->ls_cstart, h->ls_super, h->ls_cr, h->N);
+        hipLaunchKernelGGL(k_list_boxes, dim3(std::max((h->ls_ntile + 3) / 4, 4), n), dim3(256), 0, s, a, h->ls_grp);
+        const float r2 = (float)((double)h->lnp.radius * (double)h->lnp.radius);
+        const float thr = (float)((double)h->lnp.inlier_dist * 65536.0);
+        hipLaunchKernelGGL(k_list_normals, dim3((h->ls_ntile + 3) / 4, n), dim3(256), 0, s, a, o, r2, thr, h->lnp.min_points, h->lnp.min_inliers);
+    }
+    for (size_t k0 = 0; k0 < wtasks.size() && !h->list_nrm; k0 += FRAME_ARGS) {
         FrameTasks a;
         const int n = (int)std::min<size_t>(FRAME_ARGS, wtasks.size() - k0);
         for (int k = 0; k < n; ++k) a.t[k] = wtasks[k0 + k];
@@ -1951,7 +2000,31 @@ extern "C" int slam3d_icp_set_seg_params(slam3d_icp_handle *h, const slam3d_seg_
     if (!h || !seg_params_ok(sp)) return SLAM3D_E_INVALID;
     if (!is_plane(h)) return SLAM3D_E_STATE;
     h->seg_sp = *sp;
-    for (auto &fr : h->frames) { fr.nrm_epoch = 0; fr.tgt_epoch = 0; }      // normals and target tiles of every frame are stale
+    for (auto &fr : h->frames) { fr.nrm_epoch = 0; fr.tgt_epoch = 0; fr.ls_epoch[1] = 0; fr.ls_normals = -1; }   // normals and target tiles / lists of every frame are stale
+    return SLAM3D_OK;
+}
+
+// ------------------------------------------------------------------------------ spec S2l: point-list normals
+extern "C" void slam3d_list_normal_default_params(slam3d_list_normal_params *lp)
+{
+    if (!lp) return;
+    lp->radius = 0.06f;         // DESIGN.md section 3, the S2l sweep: the smallest summed translation error
+    lp->min_points = 10;
+    lp->min_inliers = 8;
+    lp->inlier_dist = 0.01f;
+}
+
+extern "C" int slam3d_icp_set_list_normal_params(slam3d_icp_handle *h, const slam3d_list_normal_params *lp)
+{
+    if (!h || !lp) return SLAM3D_E_INVALID;
+    if (!(h->p.height == 1 && h->p.width > 1)) return SLAM3D_E_STATE;       // organized: S2's windows
+    // spec S2l's exactness bound: two members of a ball differ by at most 2 r 2^16 + 1 per quantised coordinate, so with n <= LN_NMAX
+    // every entry of C' = n S2 - S1 S1^T is at most n^2 / 2 (2 r 2^16 + 1)^2 < 2^53 for r below 0.4999 m: 0.45 m is the largest radius taken
+    if (!(lp->radius > 0.0f && lp->radius <= 0.45f) || lp->min_points < 3 || lp->min_points > LN_NMAX || lp->min_inliers < 1 ||
+        lp->min_inliers > LN_NMAX || !(lp->inlier_dist > 0.0f && lp->inlier_dist <= 1.0f))
+        return SLAM3D_E_INVALID;
+    h->lnp = *lp;
+    for (auto &fr : h->frames) { fr.nrm_epoch = 0; fr.tgt_epoch = 0; fr.ls_epoch[1] = 0; fr.ls_normals = -1; }   // normals and target lists of every frame are stale
     return SLAM3D_OK;
 }
 

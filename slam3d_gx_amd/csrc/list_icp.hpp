@@ -183,6 +183,94 @@ __global__ __launch_bounds__(256) void k_list_boxes(ListTasks a, int *__restrict
     if (lane == 0) { T.box[2 * tile] = make_float4(lx, ly, lz, 0.0f); T.box[2 * tile + 1] = make_float4(hx, hy, hz, 0.0f); }
 }
 
+// (1e) spec S2l: the normal of every valid point of a list from its metric ball -- spec S2 with the 7 x 7 window
+// replaced by N(i) = { valid j : canonical d2(x_i, x_j) <= r2 }.  Runs on a sort of the frame in the NORMALS role (which == 2: every valid
+// point, tiles (1a-1d) into the handle's scratch lists, not the frame's), grid (ceil(tile capacity / 4), ntasks), block 256: one wave per
+// query tile, a lane per point.  A candidate tile counts when its box is within r of the query tile's box; lane i sums the integer moments
+// n, S1, S2 of the quantised coordinates Xq = rintf(x 2^16) of its members (doubles holding integers: exact while n < 2^13, and a point
+// with n > LN_NMAX gets no normal), solves C' = n S2 - S1 S1^T (int64, then exact in double: the radius bound of the setter keeps it
+// below 2^53) with smallest_evec3, orients it toward the camera and counts the members within inlier_dist of the plane in a second pass
+// over the same candidates.  The result goes to out[original index]; points of no tile (invalid records) keep the zeros the caller wrote.
+// Pruning is exact, with no margin needed: the box gap is formed with the canonical distance's own operations -- per axis a rounded
+// difference of two coordinates that bound the members' ones, then fma(gz, gz, fma(gy, gy, gx gx)) -- and every step is monotone, so a
+// pair of members with d2 <= r2 is never in boxes whose gap2 > r2.  The order of the list changes no bit: the moments are integer sums.
+constexpr int LN_NMAX = 2048;           // spec S2l's cap: n S2 and S1 S1^T stay below 2^62 (|Xq| < 2^20), the ball's C' below 2^53
+struct ListNrmOut { float4 *out[LS_TASKS]; };
+__global__ __launch_bounds__(256) void k_list_normals(ListTasks a, ListNrmOut o, float r2, float thr, int min_points, int min_inliers)
+{
+    __shared__ float4 s_st[4][64];
+    const int t = blockIdx.y, lane = threadIdx.x & 63, w = threadIdx.x >> 6, tile = blockIdx.x * 4 + w;
+    const ListTask &T = a.t[t];
+    const int ntiles = T.n[1];
+    if (tile >= ntiles) return;
+    const float inf = __int_as_float(0x7f800000);
+    const int2 td = T.tile[tile];
+    const bool v = lane < td.y;
+    const float4 p = v ? T.pts[td.x + lane] : make_float4(inf, inf, inf, __int_as_float(-1));
+    const float4 qlo = T.box[2 * tile], qhi = T.box[2 * tile + 1];
+    int n = 0, cnt = 0;
+    double sx = 0, sy = 0, sz = 0, sxx = 0, sxy = 0, sxz = 0, syy = 0, syz = 0, szz = 0;
+    float nxf = 0.0f, nyf = 0.0f, nzf = 0.0f, dqf = 0.0f;
+    // pass 0: moments; pass 1: inliers of the plane found in pass 0
+    auto scan = [&](int pass) __attribute__((always_inline)) {
+        for (int c0 = 0; c0 < ntiles; c0 += 64) {
+            bool hit = false;
+            if (c0 + lane < ntiles) {
+                const float4 lo = T.box[2 * (c0 + lane)], hi = T.box[2 * (c0 + lane) + 1];
+                const float gx = fmaxf(fmaxf(lo.x - qhi.x, qlo.x - hi.x), 0.0f);
+                const float gy = fmaxf(fmaxf(lo.y - qhi.y, qlo.y - hi.y), 0.0f);
+                const float gz = fmaxf(fmaxf(lo.z - qhi.z, qlo.z - hi.z), 0.0f);
+                hit = __fmaf_rn(gz, gz, __fmaf_rn(gy, gy, __fmul_rn(gx, gx))) <= r2;
+            }
+            unsigned long long m = __ballot(hit);
+            while (m != 0ull) {
+                const int k = __builtin_ctzll(m);
+                m &= m - 1ull;
+                const int2 cd = T.tile[c0 + k];
+                s_st[w][lane] = lane < cd.y ? T.pts[cd.x + lane] : make_float4(inf, inf, inf, 0.0f);
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                for (int j = 0; j < cd.y; ++j) {
+                    const float4 q = s_st[w][j];
+                    const float dx = q.x - p.x, dy = q.y - p.y, dz = q.z - p.z;
+                    const float d2 = __fmaf_rn(dz, dz, __fmaf_rn(dy, dy, __fmul_rn(dx, dx)));
+                    if (d2 <= r2) {
+                        const float xq = rintf(q.x * 65536.0f), yq = rintf(q.y * 65536.0f), zq = rintf(q.z * 65536.0f);
+                        if (pass == 0) {
+                            const double x = xq, y = yq, z = zq;
+                            ++n; sx += x; sy += y; sz += z;
+                            sxx = __fma_rn(x, x, sxx); sxy = __fma_rn(x, y, sxy); sxz = __fma_rn(x, z, sxz);
+                            syy = __fma_rn(y, y, syy); syz = __fma_rn(y, z, syz); szz = __fma_rn(z, z, szz);
+                        } else {
+                            const float e = __fmaf_rn(nzf, zq, __fmaf_rn(nyf, yq, __fmul_rn(nxf, xq))) - dqf;
+                            cnt += fabsf(e) <= thr ? 1 : 0;
+                        }
+                    }
+                }
+                __builtin_amdgcn_wave_barrier();                   // (the stage is rewritten by the next tile)
+            }
+        }
+    };
+    scan(0);
+    bool have = v && n >= min_points && n <= LN_NMAX;
+    if (have) {
+        const long long ln = n, lx = (long long)sx, ly = (long long)sy, lz = (long long)sz;
+        Sym3 C;                                                   // n S2 - S1 S1^T in int64: exact, and below 2^53
+        C.a00 = (double)(ln * (long long)sxx - lx * lx); C.a01 = (double)(ln * (long long)sxy - lx * ly); C.a02 = (double)(ln * (long long)sxz - lx * lz);
+        C.a11 = (double)(ln * (long long)syy - ly * ly); C.a12 = (double)(ln * (long long)syz - ly * lz); C.a22 = (double)(ln * (long long)szz - lz * lz);
+        double nx, ny, nz;
+        have = smallest_evec3(C, nx, ny, nz);
+        const double px = rintf(p.x * 65536.0f), py = rintf(p.y * 65536.0f), pz = rintf(p.z * 65536.0f);
+        if ((nx * px + ny * py) + nz * pz > 0.0) { nx = -nx; ny = -ny; nz = -nz; }      // toward the camera
+        const double inv = 1.0 / (double)n;
+        dqf = (float)((nx * (sx * inv) + ny * (sy * inv)) + nz * (sz * inv));          // the LS plane passes through the ball's mean
+        nxf = (float)nx; nyf = (float)ny; nzf = (float)nz;
+    }
+    if (__ballot(have) != 0ull) scan(1);
+    if (v) o.out[t][__float_as_int(p.w)] = (have && cnt >= min_inliers) ? make_float4(nxf, nyf, nzf, 1.0f) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+}
+
 // (2) the persistent launch: grid (G <= LS_MAX_BLOCKS / B, B), block 64 x LS_WAVES.  `ticket[b]` (zeroed by k_pair_init) is the pair's
 // barrier counter: iteration `it` is complete when it reads (it + 1) * G.
 //

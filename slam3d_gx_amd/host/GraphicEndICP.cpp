@@ -88,10 +88,25 @@ void GraphicEndICP::init(const string &param_file)
     _grid_leaf = (float)_reader->GetDouble("grid_leaf", 0.03);                         // :288
     // icp_cloud: depth (default) -- multiPnP aligns the organized depth frames;  voxel -- it aligns the cloud readimage made of the
     // frame (PCD -> PassThrough -> VoxelGrid, ~15 k points; needs icp_read_pcd: yes), which is what the reference hands on
-    // (src/GraphicEnd.cpp:279-295 -> :158): point lists, svd estimator, one persistent launch per alignment (csrc/list_icp.hpp)
+    // (src/GraphicEnd.cpp:279-295 -> :158): point lists, one persistent launch per alignment (csrc/list_icp.hpp), svd unless icp_cloud_estimator says otherwise
     _cloud_voxel = _reader->Has("icp_cloud") && _reader->GetPara("icp_cloud") == "voxel";
     _cloud_max_points = _reader->GetInt("icp_cloud_max_points", 32768);
     if (_cloud_voxel && !_read_pcd) { cerr << "icp_cloud: voxel needs icp_read_pcd: yes (the voxel cloud is made from the frame's PCD file)" << endl; exit(1); }
+    // icp_cloud_estimator: svd (default) | point2plane | plane -- the estimator of the point lists; point2plane / plane take a list point's
+    // normal from its metric ball (DESIGN.md spec S2l, pcl::NormalEstimation with a radius search), keys icp_list_normal_radius /
+    // _min_points / _min_inliers / _inlier_dist; plane reads icp_plane_only / icp_plane_pair_gate as the organized handle does
+    slam3d_list_normal_default_params(&_list_normals);
+    if (_reader->Has("icp_cloud_estimator")) {
+        const string ce = _reader->GetPara("icp_cloud_estimator");
+        if (ce == "svd") _cloud_estimator = SLAM3D_EST_SVD;
+        else if (ce == "point2plane") _cloud_estimator = SLAM3D_EST_POINT2PLANE;
+        else if (ce == "plane") _cloud_estimator = SLAM3D_EST_PLANE;
+        else { cerr << "icp_cloud_estimator: unknown value '" << ce << "' (svd | point2plane | plane)" << endl; exit(1); }
+    }
+    _list_normals.radius = (float)_reader->GetDouble("icp_list_normal_radius", _list_normals.radius);
+    _list_normals.min_points = _reader->GetInt("icp_list_normal_min_points", _list_normals.min_points);
+    _list_normals.min_inliers = _reader->GetInt("icp_list_normal_min_inliers", _list_normals.min_inliers);
+    _list_normals.inlier_dist = (float)_reader->GetDouble("icp_list_normal_inlier_dist", _list_normals.inlier_dist);
     _extract_planes = _reader->Has("icp_extract_planes") && _reader->GetPara("icp_extract_planes") == "yes";
     slam3d_seg_default_params(&_seg);
     _seg.distance_threshold = (float)_reader->GetDouble("distance_threshold", 0.08);   // src/GraphicEnd.cpp:89
@@ -179,11 +194,29 @@ void GraphicEndICP::init(const string &param_file)
         if (_cloud_voxel) {
             slam3d_icp_params lp = _params;
             lp.width = _cloud_max_points; lp.height = 1;
-            lp.estimator = SLAM3D_EST_SVD; lp.plane_flags = 0;                 // a list has no 7x7 windows: point-to-point (Kabsch)
-            lp.max_plane_residual2 = 0.0f; lp.min_normal_cos = 0.0f;
+            lp.estimator = _cloud_estimator; lp.plane_flags = 0;
+            if (_cloud_estimator != SLAM3D_EST_SVD) lp.normal_window = 0;      // a list has no image window: ball normals (spec S2l)
+            if (_cloud_estimator == SLAM3D_EST_PLANE) {
+                if (_reader->Has("icp_plane_pair_gate") && _reader->GetPara("icp_plane_pair_gate") == "yes") lp.plane_flags |= SLAM3D_PLANE_PAIR_GATE;
+                if (_reader->Has("icp_plane_only") && _reader->GetPara("icp_plane_only") == "yes") lp.plane_flags |= SLAM3D_PLANE_ONLY;
+            }
+            if (_cloud_estimator == SLAM3D_EST_SVD) { lp.max_plane_residual2 = 0.0f; lp.min_normal_cos = 0.0f; }     // (gates of the point-to-plane rows)
             lp.nn_mode = SLAM3D_NN_AUTO;
             const int lrc = slam3d_icp_create(&lp, &d.icp_list);
             if (lrc != SLAM3D_OK) { cerr << "slam3d_icp_create (point lists, device " << d.device << ") failed: " << slam3d_strerror(lrc) << endl; exit(1); }
+            if (_cloud_estimator != SLAM3D_EST_SVD) {
+                int nrc = slam3d_icp_set_list_normal_params(d.icp_list, &_list_normals);
+                if (nrc == SLAM3D_OK && _cloud_estimator == SLAM3D_EST_PLANE) {
+                    slam3d_seg_params sp = _seg;
+                    sp.seed = 1;
+                    sp.distance_threshold = (float)_reader->GetDouble("icp_seg_distance_threshold", 0.04);
+                    nrc = slam3d_icp_set_seg_params(d.icp_list, &sp);
+                }
+                if (nrc != SLAM3D_OK) {
+                    cerr << "icp_list_normal_* / plane parameters of the point lists out of the library's range: " << slam3d_strerror(nrc) << endl;
+                    exit(1);
+                }
+            }
         }
         d.first_frame = 2 * _max_batch;
         d.key.assign(_params.extra_frames, -1);

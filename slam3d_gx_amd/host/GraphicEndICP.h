@@ -129,6 +129,8 @@ class GraphicEndICP {
     slam3d_seg_params _seg;
     std::ofstream _lcfile, _planefile;
     bool _read_pcd = false;
+    int _cloud_estimator = SLAM3D_EST_SVD;    // icp_cloud_estimator: svd | point2plane | plane (point lists)
+    slam3d_list_normal_params _list_normals;  // icp_list_normal_* (spec S2l)
     bool _cloud_voxel = false;        // icp_cloud: voxel -- multiPnP aligns readimage's voxel clouds (point lists), as the reference hands them on (src/GraphicEnd.cpp:158)
     int _cloud_max_points = 32768;    // icp_cloud_max_points: capacity of the point-list handle
     std::string _pclPath;
